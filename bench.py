@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — scenes/s of the relevancy -> fusion -> OVSSC hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]        (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 A "step" is ONE synthetic scene end to end on one GPU: 480x480 RGB-D, 16 labels, ViT-B/16, the "ours" saliency config
 (204 tiles x 6 images (5 colour-jitter copies) x 2 flips = 2 448 ViT forwards), analytic attention x gradient rollout,
@@ -10,9 +10,12 @@ volumes of 128^3, implicit decoder at the 128^3 voxel centres, TSDF integration 
 (uint8 images, fp32 depth, weights) are resident in HBM before the timed region.  Ranks process disjoint scenes
 (scene sharding, no data-path collective) -> weak scaling; value = all scenes / max-over-ranks time.
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel = the fp16 MFMA GEMM, timed
-live inside the timed region with HIP events carried by the launches' own dispatch packets) and `cpu_baseline` (the oracle on the host cores, bounded
-sample, N = 1).
+Prints ONE JSON line (rank 0) with the contract fields.  A plain run does only what `value` and `ms_per_step` need: set-up, W warm-up steps,
+K timed steps.  --full adds `roofline` (dominant kernel = the fp16 MFMA GEMM, timed live inside the timed region with HIP events carried by the
+launches' own dispatch packets, and the clock / power sampled meanwhile) and, N = 1, after the timed region: `parity` (reference goldens), `stages`
+(the other BASELINE configs and the per-kernel-class table) and `cpu_baseline` (the oracle on the host cores, bounded sample).
+--dump-outputs DIR writes the arrays the last timed step handed back as DIR/<name>.npy (float32 / float64, 64 MB at most; the inputs are seeded, so
+two builds can be compared output for output).
 """
 from __future__ import annotations
 
@@ -373,6 +376,49 @@ class SmiSampler:
                             "the UNet / attention / LayerNorm phases draw less than the GEMM phases, so the GEMM-only figures are at or above these"}
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6                                   # --dump-outputs: all arrays together
+DUMP_SAMPLE = 1 << 18                                             # voxel columns of the [L, S^3] logits (and 4 x as many parameters) written
+
+
+def _sample_idx(n, k, seed=0):
+    """A fixed, seeded, sorted sample of k of n indices (all of them when k >= n)."""
+    return np.sort(np.random.default_rng(seed).choice(n, size=min(k, n), replace=False))
+
+
+def scene_outputs(res):
+    """The arrays ScenePipeline.run hands its caller (SceneResult), as host float32 / float64: the logits as a sample of voxel columns (all labels)."""
+    idx = _sample_idx(res.logits.shape[1], DUMP_SAMPLE)
+    out = {"relevancies": res.relevancies.float().cpu().numpy(),
+           "logits_sample": res.logits[:, torch.from_numpy(idx).to(res.logits.device)].float().cpu().numpy(),
+           "logits_sample_voxels": idx.astype(np.float64),
+           "n_in": res.n_in.cpu().numpy().astype(np.float64)}
+    if res.labels is not None:
+        out["labels"] = res.labels.cpu().numpy().astype(np.float32)               # -1 .. L - 1: exact in float32
+    if res.tsdf is not None:
+        out["tsdf"] = res.tsdf.float().cpu().numpy()
+    return out
+
+
+def train_outputs(tr, out):
+    """What VOOLTrainer.step hands its caller (loss, logits, gradient norm) and a sample of the parameters it updated (flattened in `tr.params` order)."""
+    flat = torch.cat([p.detach().reshape(-1) for p in tr.params.values()])
+    idx = _sample_idx(flat.numel(), 4 * DUMP_SAMPLE)
+    return {"loss": np.asarray([float(out["loss"])], np.float64), "gradnorm": np.asarray([float(out["gradnorm"])], np.float64),
+            "logits": out["logits"].float().cpu().numpy(), "params_sample": flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy(),
+            "params_sample_idx": idx.astype(np.float64)}
+
+
+def dump_outputs(dirname, arrays):
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    bad = [k for k, v in arrays.items() if v.dtype not in (np.float32, np.float64)]
+    total = sum(v.nbytes for v in arrays.values())
+    if bad or total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {bad} not float32 / float64, or {total} bytes > {DUMP_LIMIT_BYTES}")
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+
+
 HBM_PEAK_TBS = 8.0                                                # HBM3E spec (MI355X_MICROARCH.md); ~6.3 TB/s is what a copy reaches
 HBM_COPY_TBS = 6.3                                                # what a float4 copy kernel reaches on this part (same guide)
 EPI_NAMES = {0: "bias -> fp16", 1: "bias + QuickGELU -> fp16", 2: "bias + fp32 residual read-modify-write", 3: "bias -> fp32", 4: "row-remapped fp32", 5: "row-table multiply -> fp16"}
@@ -654,6 +700,8 @@ def train_workload(args, rank, world, dist):
     if dist is not None:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, train_outputs(tr, out))
     ar_ms = None
     per_rank = None
     if dist is not None:
@@ -699,6 +747,49 @@ def train_workload(args, rank, world, dist):
         dist.destroy_process_group()
 
 
+def roofline_report(gs, dt, world, time_every, smi):
+    """--full: the fp16 GEMM class over the timed region (GemmTimer events) against the MFMA peak, with the clock / power sampled meanwhile."""
+    ach = gs["flops"] / (gs["total_ms"] * 1e-3) / 1e12 if gs["total_ms"] > 0 else 0.0
+    # HBM bytes per GEMM launch: PMC counters cannot be read from inside the process that is being timed (rocprofv3 owns them and
+    # serialises the kernels), so this figure is IMPORTED from the committed counter run of this same command and labelled as such
+    traffic, traffic_src = None, None
+    for name in ("r06_gemm_pmc.json", "r05_gemm_pmc.json"):
+        pmc = os.path.join(ROOT, "profiles", name)
+        if os.path.exists(pmc):
+            try:
+                traffic = json.load(open(pmc)).get("hbm_bytes_per_launch")
+                traffic_src = f"imported from profiles/{name} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command; FETCH_SIZE x 2 per the gfx950 correction), not measured in this run"
+                break
+            except Exception:
+                traffic = None
+    out = {"kernel": "fp16 GEMM: k_gemm8 (large shapes) + k_gemm_f16 (small), all epilogues", "bound": "mfma", "achieved": ach, "peak": PEAK_F16_TFLOPS, "unit": "TFLOP/s",
+           "frac": ach / PEAK_F16_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
+           "algorithmic_bytes_per_launch": gs["bytes"] / max(1, gs["launches"]),
+           "traffic_over_algorithmic": (traffic / (gs["bytes"] / max(1, gs["launches"]))) if (traffic and gs["bytes"]) else None,
+           "algorithmic_bytes_note": "A + W + C per launch (fp16 operands; C fp16 2 B, fp32 4 B, fp32 residual read-modify-write 8 B per element), averaged over the timed launches",
+           "launches": gs["launches"], "launches_in_timed_region": gs["seen"],
+           "sampling": ("every GEMM launch of the timed region carries start / stop events" if time_every == 1 else
+                        f"1 in {time_every} GEMM launches of the timed region (hashed launch index) carries start / stop events"),
+           "avg_launch_us": gs["total_ms"] * 1e3 / max(1, gs["launches"]),
+           "per_shape": {gemm_shape_name(k[0], k[1], k[2]): {"launches": v[0], "avg_us": round(v[1] * 1e3 / v[0], 1), "tflops": round(v[2] / v[1] / 1e9, 1),
+                                                               "roof_us": round(gemm_roof_ms(v[2] / v[0], v[3] / v[0])[0] * 1e3, 1), "bound": gemm_roof_ms(v[2] / v[0], v[3] / v[0])[1],
+                                                               "frac_of_roof": round(gemm_roof_ms(v[2] / v[0], v[3] / v[0])[0] * v[0] / v[1], 3)}
+                         for k, v in sorted(gs["shapes"].items(), key=lambda kv: -kv[1][1]) if v[1] > 0},
+           "frac_of_per_launch_roofs": (sum(gemm_roof_ms(v[2] / v[0], v[3] / v[0])[0] * v[0] for v in gs["shapes"].values() if v[0]) / gs["total_ms"]) if gs["total_ms"] > 0 else None,
+           "gemm_share_of_step": gs["total_ms"] * 1e-3 * gs["seen"] / max(1, gs["launches"]) / dt if world == 1 else None,
+           }
+    out.update(smi.summary())
+    # context beside `frac` (which stays against the 2.4 GHz dense peak): the same achieved rate against the peak at the shader clock the part actually held
+    # during the timed region - at its power cap the part clocks down under matrix load, so this is the fraction of the matrix pipe's cycles that did work
+    sclk = out.get("sclk_mhz_under_load")
+    if sclk:
+        out["peak_at_measured_sclk"] = PEAK_F16_TFLOPS * float(sclk) / 2400.0
+        out["frac_at_measured_sclk"] = ach / (PEAK_F16_TFLOPS * float(sclk) / 2400.0)
+        out["frac_at_measured_sclk_note"] = ("achieved / (peak x sclk_mhz_under_load / 2400): the scene-wide median clock; the GEMM phases alone hold a LOWER "
+                                             "clock than the median (profiles/r04_mfma_probes.txt), so this is a lower bound of the matrix pipe's busy fraction")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -727,10 +818,15 @@ def main():
                     "ranks may share one device (contract tests on a 1-GPU box; device collectives are staged through the host)")
     ap.add_argument("--cu-split", default="0", help="throughput mode: N[:layout] = run scene i's voxel stage on a stream masked to N CUs concurrently with scene "
                     "i + 1's relevancy stage on the remaining CUs (semabs_amd.scene.CuPartition; layout balanced | low).  0 (default) = one stream, stages in sequence")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the parity leg (reference goldens, outside the timed region)")
-    ap.add_argument("--no-stages", action="store_true", help="skip the stage / kernel-class leg (configs 2, 3, 5 and the per-class table, outside the timed region)")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure: the roofline and clock / power sampling of the timed region "
+                    "and, N = 1, the parity, stage / kernel-class and CPU-baseline legs after it (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the arrays the last timed step handed back as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU-baseline leg")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the parity leg (reference goldens, outside the timed region)")
+    ap.add_argument("--no-stages", action="store_true", help="--full: skip the stage / kernel-class leg (configs 2, 3, 5 and the per-class table, outside the timed region)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a HIP device (MI355X); there is no CPU fallback")
@@ -834,12 +930,12 @@ def main():
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
-    timer = vitmod.GemmTimer(every=args.time_every)
+    timer = vitmod.GemmTimer(every=args.time_every) if args.full else None
     vitmod.GEMM_TIMER = timer
     if dist is not None:
         from semabs_amd import dist as _sdist
         _sdist.reset_stats()
-    smi = SmiSampler(local) if rank == 0 else None
+    smi = SmiSampler(local) if rank == 0 and args.full else None
     torch.cuda.synchronize()
     if smi is not None:
         smi.start()
@@ -862,7 +958,9 @@ def main():
         t = torch.tensor([dt], device="cpu" if args.backend == "gloo" else "cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    gs = timer.summary()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, scene_outputs(res))
+    gs = timer.summary() if timer is not None else None
     total_scenes = args.steps * (1 if latency else world)
     value = total_scenes / dt
     wire = None
@@ -895,19 +993,6 @@ def main():
         if gathered is not None:
             wire["gathered_label_volumes_checksum"] = digest(gathered)
     if rank == 0:
-        ach = gs["flops"] / (gs["total_ms"] * 1e-3) / 1e12 if gs["total_ms"] > 0 else 0.0
-        # HBM bytes per GEMM launch: PMC counters cannot be read from inside the process that is being timed (rocprofv3 owns them and
-        # serialises the kernels), so this figure is IMPORTED from the committed counter run of this same command and labelled as such
-        traffic, traffic_src = None, None
-        for name in ("r06_gemm_pmc.json", "r05_gemm_pmc.json"):
-            pmc = os.path.join(ROOT, "profiles", name)
-            if os.path.exists(pmc):
-                try:
-                    traffic = json.load(open(pmc)).get("hbm_bytes_per_launch")
-                    traffic_src = f"imported from profiles/{name} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command; FETCH_SIZE x 2 per the gfx950 correction), not measured in this run"
-                    break
-                except Exception:
-                    traffic = None
         out = {
             "metric": "scenes/sec (relevancy+3D-UNet infer), 480x480x16-label x128^3" + (" - single-scene LATENCY mode: every scene tile- and label-sharded over all ranks" if latency else ""),
             "value": value, "unit": "scenes/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -920,32 +1005,9 @@ def main():
                        "mode": args.mode, "backend": args.backend if world > 1 else None,
                        "cu_split": None if part is None else {"voxel_cus": part.cus[0], "vit_cus": part.cus[1], "layout": part.layout}},
             "relevancy_tflops_algorithmic": 2448 * FLOPS_PER_TILE[args.arch] * total_scenes / dt / 1e12,
-            "roofline": {"kernel": "fp16 GEMM: k_gemm8 (large shapes) + k_gemm_f16 (small), all epilogues", "bound": "mfma", "achieved": ach, "peak": PEAK_F16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": ach / PEAK_F16_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": gs["bytes"] / max(1, gs["launches"]),
-                         "traffic_over_algorithmic": (traffic / (gs["bytes"] / max(1, gs["launches"]))) if (traffic and gs["bytes"]) else None,
-                         "algorithmic_bytes_note": "A + W + C per launch (fp16 operands; C fp16 2 B, fp32 4 B, fp32 residual read-modify-write 8 B per element), averaged over the timed launches",
-                         "launches": gs["launches"], "launches_in_timed_region": gs["seen"],
-                         "sampling": ("every GEMM launch of the timed region carries start / stop events" if args.time_every == 1 else
-                                      f"1 in {args.time_every} GEMM launches of the timed region (hashed launch index) carries start / stop events"),
-                         "avg_launch_us": gs["total_ms"] * 1e3 / max(1, gs["launches"]),
-                         "per_shape": {gemm_shape_name(k[0], k[1], k[2]): {"launches": v[0], "avg_us": round(v[1] * 1e3 / v[0], 1), "tflops": round(v[2] / v[1] / 1e9, 1),
-                                                                             "roof_us": round(gemm_roof_ms(v[2] / v[0], v[3] / v[0])[0] * 1e3, 1), "bound": gemm_roof_ms(v[2] / v[0], v[3] / v[0])[1],
-                                                                             "frac_of_roof": round(gemm_roof_ms(v[2] / v[0], v[3] / v[0])[0] * v[0] / v[1], 3)}
-                                       for k, v in sorted(gs["shapes"].items(), key=lambda kv: -kv[1][1]) if v[1] > 0},
-                         "frac_of_per_launch_roofs": (sum(gemm_roof_ms(v[2] / v[0], v[3] / v[0])[0] * v[0] for v in gs["shapes"].values() if v[0]) / gs["total_ms"]) if gs["total_ms"] > 0 else None,
-                         "gemm_share_of_step": gs["total_ms"] * 1e-3 * gs["seen"] / max(1, gs["launches"]) / dt if world == 1 else None,
-                         },
         }
-        out["roofline"].update(smi.summary())
-        # context beside `frac` (which stays against the 2.4 GHz dense peak): the same achieved rate against the peak at the shader clock the part actually held
-        # during the timed region - at its power cap the part clocks down under matrix load, so this is the fraction of the matrix pipe's cycles that did work
-        sclk = out["roofline"].get("sclk_mhz_under_load")
-        if sclk:
-            out["roofline"]["peak_at_measured_sclk"] = PEAK_F16_TFLOPS * float(sclk) / 2400.0
-            out["roofline"]["frac_at_measured_sclk"] = ach / (PEAK_F16_TFLOPS * float(sclk) / 2400.0)
-            out["roofline"]["frac_at_measured_sclk_note"] = ("achieved / (peak x sclk_mhz_under_load / 2400): the scene-wide median clock; the GEMM phases alone hold a LOWER "
-                                                             "clock than the median (profiles/r04_mfma_probes.txt), so this is a lower bound of the matrix pipe's busy fraction")
+        if gs is not None:
+            out["roofline"] = roofline_report(gs, dt, world, args.time_every, smi)
         out["timed_region"] = ("per scene, everything from the uint8 frame + fp32 depth resident in HBM to the label volume: " +
                                ("the text tower on the 16 labels' token ids (the reference encodes the label set on every get_clip_saliency call), " if text_enc is not None else "") +
                                "colour jitter, tiling, ViT + rollout, aggregation, unprojection + compaction + sub-sample, point MLP, scatter, UNet, decoder, TSDF, "
@@ -959,11 +1021,11 @@ def main():
             wire["exposed_ms_note"] = ("device time the compute stream spent inside the (blocking) all-gathers of the timed region, per step, maximum over the ranks - HIP events "
                                        "around each call (semabs_amd.dist); scene-shard mode has ONE gather of the final label volumes in the whole run")
             out["collectives"] = wire
-        if world == 1 and not args.no_parity:
+        if world == 1 and args.full and not args.no_parity:
             out["parity"] = parity_report(pipe, args.arch, args.precision)
-        if world == 1 and not args.no_stages:
+        if world == 1 and args.full and not args.no_stages:
             out["stages"] = stage_report(pipe, scenes, w_text, args.arch, args.precision)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.arch, N_LABELS)
         print(json.dumps(out), flush=True)
     if dist is not None:

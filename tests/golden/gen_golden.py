@@ -1352,3 +1352,55 @@ if __name__ == "__main__" and any(a.startswith("g29") for a in sys.argv[1:]):
 
 if __name__ == "__main__" and "g30" in sys.argv[1:]:
     g9_semabs3d(stats="trained", name="g30_semabs3d_trained")
+
+
+# ---- appended: the part of CLIP's BPE merge table the tokenizer tests consult (third-party data, 1.3 MB, not carried whole) -----------------
+def bpe_tokenizer_test_texts():
+    """Every string the tokenizer tests and the token fixtures encode."""
+    from semabs_amd.clip import imagenet_templates
+    labels = ["chair", "table", "pink make up bag", "brown modern upholstered chair in faux leather with wooden legs"]
+    texts = [t.format(c) for c in labels for t in ["a photo of a {}.", "a bad photo of the {}.", DEFAULT_PROMPT]]
+    texts += ["Hello, World! it's 42 degrees", "a  b\tc", "don't you're we've", "word " * 100]
+    texts += [t.format(str(c)) for c in np.load(os.path.join(HERE, "g24_prompt_ensemble.npz"))["labels"] for t in imagenet_templates]
+    g = np.load(os.path.join(HERE, "tokens_default.npz"))
+    return texts + [str(g["prompt"]).format(str(c)) for c in g["labels"]]
+
+
+def bpe_merges_subset():
+    """Runs the product tokenizer on the full table over `bpe_tokenizer_test_texts()` and keeps every merge it looks up and finds, and every
+    merged symbol it emits, with its rank; checks that the table rebuilt from the subset gives the same ids."""
+    import tempfile
+    sys.path.insert(0, os.path.dirname(HERE))
+    from _bpe_table import N_MERGES, write_table
+    from semabs_amd.clip.tokenizer import BPETokenizer
+    tk = BPETokenizer(os.path.join(refimport.REF, "CLIP", "clip", "bpe_simple_vocab_16e6.txt.gz"))
+    by_rank = {r: " ".join(m) for m, r in tk.rank.items()}
+    used = set()
+
+    class Ranks(dict):
+        def get(self, k, default=None):
+            r = dict.get(self, k, default)
+            if r is not None:
+                used.add(r)
+            return r
+
+    class Ids(dict):
+        def __getitem__(self, s):
+            i = dict.__getitem__(self, s)
+            if 512 <= i < 512 + N_MERGES:
+                used.add(i - 512)
+            return i
+
+    tk.rank, tk.ids = Ranks(tk.rank), Ids(tk.ids)
+    texts = bpe_tokenizer_test_texts()
+    full = tk.tokenize(texts, truncate=True).numpy()
+    ranks = np.asarray(sorted(used), np.int32)
+    merges = np.asarray([by_rank[int(r)] for r in ranks])
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "bpe.txt.gz")
+        assert np.array_equal(BPETokenizer(write_table(path, ranks, merges)).tokenize(texts, truncate=True).numpy(), full)
+    save("bpe_merges_subset", ranks=ranks, merges=merges)
+
+
+if __name__ == "__main__" and "bpe" in sys.argv[1:]:
+    bpe_merges_subset()

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -21,7 +22,7 @@ def test_bench_refuses_to_run_without_a_gpu():
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--no-cpu-baseline"], cwd=ROOT,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"], cwd=ROOT,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -60,6 +61,30 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
             assert abs(rf["frac_at_measured_sclk"] * rf["peak_at_measured_sclk"] - rf["achieved"]) < 1e-6 * rf["achieved"]
             assert abs(rf["peak_at_measured_sclk"] - rf["peak"] * rf["sclk_mhz_under_load"] / 2400.0) < 1e-6 * rf["peak"]
             assert abs(rf["frac"] * rf["peak"] - rf["achieved"]) < 1e-6 * rf["achieved"]
+
+
+@pytest.mark.gpu
+def test_plain_bench_runs_its_steps_only_and_dumps_the_last_steps_outputs(tmp_path):
+    """Without --full the line carries the contract fields and nothing measured outside the timed steps; --dump-outputs writes what the last timed
+    step handed back (ScenePipeline.run's SceneResult, the logits as a seeded sample of voxel columns) as float32 / float64 .npy, 64 MB at most."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")], cwd=ROOT,
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["config"]["scenes_per_gpu"] == 2 and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert d["unit"] == "scenes/s" and d["higher_is_better"] is True and "dtype" in d and d.get("text_tower_in_timed_region") is True
+    assert not {"roofline", "parity", "stages", "cpu_baseline"} & set(d)
+    a = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert set(a) == {"relevancies", "logits_sample", "logits_sample_voxels", "labels", "tsdf", "n_in"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64e6
+    assert a["relevancies"].shape == (16, 480, 480) and a["labels"].shape == (128 ** 3,) and a["tsdf"].shape == (128, 128, 128)
+    assert a["logits_sample"].shape == (16, len(a["logits_sample_voxels"])) and np.isfinite(a["logits_sample"]).all() and a["n_in"][0] > 0
+    # the labels are the argmax of the logits wherever a voxel is labelled (-1 = masked out)
+    lab = a["labels"][a["logits_sample_voxels"].astype(np.int64)]
+    keep = lab >= 0
+    assert keep.any() and np.array_equal(lab[keep], a["logits_sample"][:, keep].argmax(0))
 
 
 @pytest.mark.gpu

@@ -287,12 +287,10 @@ def test_text_tower(golden):
         assert np.abs(w - ref).max() <= 5e-3 * np.abs(ref).max(), np.abs(w - ref).max()
 
 
-def test_tokenizer_matches_reference_ids(golden):
-    from semabs_amd.clip.tokenizer import BPETokenizer, find_vocab
-    if find_vocab() is None:
-        pytest.skip("CLIP BPE merge table not available on this box (third-party data, not carried by the repo)")
+def test_tokenizer_matches_reference_ids(golden, bpe_vocab):
+    from semabs_amd.clip.tokenizer import BPETokenizer
     g = golden("g7_text")
-    tk = BPETokenizer()
+    tk = BPETokenizer(bpe_vocab)
     labels = ["chair", "table", "pink make up bag", "brown modern upholstered chair in faux leather with wooden legs"]
     assert np.array_equal(tk.tokenize([DEFAULT_PROMPT.format(c) for c in labels]).numpy(), g["t1_tokens"])
     assert np.array_equal(tk.tokenize(["Hello, World! it's 42 degrees", "a  b\tc", "don't you're we've"]).numpy(), g["misc_tokens"])

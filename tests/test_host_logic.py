@@ -42,12 +42,10 @@ def test_duplicate_tile_size_rejected():
         plan_tiles(64, 64, 1, [{"tile_size": 32, "stride": 8}, {"tile_size": 32, "stride": 16}])
 
 
-def test_tokenizer_against_golden(golden):
-    from semabs_amd.clip.tokenizer import BPETokenizer, find_vocab
-    if find_vocab() is None:
-        pytest.skip("CLIP BPE merge table not present")
+def test_tokenizer_against_golden(golden, bpe_vocab):
+    from semabs_amd.clip.tokenizer import BPETokenizer
     g = golden("g7_text")
-    tk = BPETokenizer()
+    tk = BPETokenizer(bpe_vocab)
     labels = ["chair", "table", "pink make up bag", "brown modern upholstered chair in faux leather with wooden legs"]
     P = "a photograph of a {} in a home."
     assert np.array_equal(tk.tokenize([P.format(c) for c in labels]).numpy(), g["t1_tokens"])
@@ -72,14 +70,12 @@ def test_imagenet_templates_table_and_reference_import_line(golden):
     assert all(cfg(480)["imagenet_prompt_ensemble"] is False for cfg in saliency_configs.values())
 
 
-def test_tokenizer_on_the_prompt_ensemble(golden):
+def test_tokenizer_on_the_prompt_ensemble(golden, bpe_vocab):
     from semabs_amd.clip import imagenet_templates
-    from semabs_amd.clip.tokenizer import BPETokenizer, find_vocab
-    if find_vocab() is None:
-        pytest.skip("CLIP BPE merge table not present")
+    from semabs_amd.clip.tokenizer import BPETokenizer
     g = golden("g24_prompt_ensemble")
     texts = [t.format(c) for c in [str(l) for l in g["labels"]] for t in imagenet_templates]
-    assert np.array_equal(BPETokenizer().tokenize(texts).numpy(), g["tokens"])
+    assert np.array_equal(BPETokenizer(bpe_vocab).tokenize(texts).numpy(), g["tokens"])
 
 
 def test_shard_range_partitions():

@@ -19,7 +19,8 @@ import torch
 from . import _lib
 from .net import VirtualGrid
 from .optim import Lamb
-from .unet3d import number_of_features_per_level
+from .unet3d import (_Conv, _ConvT, _Rec, conv_bwd_layout, conv_fwd_layout, convT_class_layout, gn_conv, linear_layout,
+                     number_of_features_per_level, unet_forward)
 from .weights import unet_layer_plan
 
 RELATIONS = ["in", "behind", "in front of", "on the left of", "on the right of", "on", "[pad]"]
@@ -34,26 +35,9 @@ TAPS_CONV3 = _taps([(a - 1, b - 1, c - 1) for a in range(3) for b in range(3) fo
 TAPS_ONE = _taps([(0, 0, 0)])
 
 
-def _pad32(w: torch.Tensor) -> torch.Tensor:
-    kp = (w.shape[1] + 31) // 32 * 32
-    if kp == w.shape[1]:
-        return w.contiguous()
-    out = torch.zeros(w.shape[0], kp, dtype=w.dtype, device=w.device)
-    out[:, : w.shape[1]] = w
-    return out
-
-
-def _flat_packed(w: torch.Tensor):
-    """[rows, Kp] -> (flat = the matrix followed by its fragment-packed copy when the shape allows, flag word)."""
-    from .unet3d import _pack_fragments
-    if w.shape[0] % 16 == 0 and w.shape[1] % 32 == 0:
-        return torch.cat([w.reshape(-1), _pack_fragments(w)]), 512
-    return w.reshape(-1), 0
-
-
 class _WeightLayouts:
     """Split-fp16 kernel operands of the trainable weights, refreshed every step by index gathers (semabs_gather_split16).
-    `build(t)` is the layout written with torch data-movement ops (permute / flip / cat / zero padding) - it is run ONCE on an index tensor
+    `build(t) -> (flat, *extra)` is one of unet3d's layout functions (torch data-movement ops only) - it is run ONCE on an index tensor
     (1 .. numel, zeros = padding) to obtain the int32 map, and the hi / lo buffers keep their addresses for the lifetime of the trainer.
     Round 6: `refresh_all()` at the start of a step re-gathers EVERY registered layout in one launch (semabs_gather_split16_batched: 78 launches of 5 - 60 us
     before); `get()` then only hands out the buffers.  A layout that is new, or whose source tensor moved, is gathered on the spot and joins the table."""
@@ -89,14 +73,14 @@ class _WeightLayouts:
         m = self.maps.get(key)
         if m is None or m[3] != tuple(w.shape):
             ar = torch.arange(1, w.numel() + 1, dtype=torch.int32, device=self.dev).view(w.shape)
-            out = build(ar)
-            flat, extra = (out if isinstance(out, tuple) else (out, None))
+            flat, *extra = build(ar)
             idx = (flat.reshape(-1) - 1).to(torch.int32).contiguous()
             hi = torch.empty(idx.numel(), dtype=torch.float16, device=self.dev)
             lo = torch.empty_like(hi)
             m = (idx, hi, lo, tuple(w.shape), extra)
             self.maps[key] = m
             self.fresh.discard(key)
+            self._table = None               # the batched job table holds raw pointers of the buffers just created / replaced
         idx, hi, lo, _, extra = m
         src = w.detach()
         assert src.is_contiguous() and src.dtype == torch.float32
@@ -104,7 +88,7 @@ class _WeightLayouts:
             self.src_ptr[key] = src.data_ptr()
             _lib.call("semabs_gather_split16", _lib.ptr(src), _lib.ptr(idx), idx.numel(), _lib.ptr(hi), _lib.ptr(lo), _lib.stream())
             self.fresh.add(key)
-        return hi, lo, extra
+        return (hi, lo, *extra)
 
 
 class _ZeroArena:
@@ -129,11 +113,6 @@ class _ZeroArena:
         return self.buf[o:o + n].view(dtype).view(*shape)
 
 
-class _Rec:
-    """Tape entry of one GroupNorm + Conv3d: what the backward pass needs."""
-    __slots__ = ("name", "x", "y", "mean", "rstd", "scale", "shift")
-
-
 class UNetTrainer:
     """Forward-with-tape and backward of ResidualUNet3D (unet3d.py:190-259, 596-621), channels-last fp32."""
 
@@ -144,18 +123,16 @@ class UNetTrainer:
         self.f_maps = list(f_maps)
         self.p, self.g, self.prefix, self.G = params, grads, prefix, num_groups
         self.plan = unet_layer_plan(in_channels, out_channels, self.f_maps[0], len(self.f_maps))
-        self.mats: Dict[str, dict] = {}
+        self.convs, self.enc, self.dec = {}, [], []      # key prefix -> _Conv / _ConvT operand record (with .bwd); the same in walk order: see refresh()
         self.dev = _lib.require_gpu()
         self._wgs = None
-        self._wg_routes = {}
+        self._routes = {}
         self.rows_linear = os.environ.get("SEMABS_ROWS_LINEAR", "1") == "1"      # 1 x 1 x 1 convolutions / MLP layers on semabs_linear_rows
         self.wgrad_tr = os.environ.get("SEMABS_WGRAD_TR", "1") == "1"      # A/B: 0 = the round-2 brick kernel (transposes while staging, atomics)
         # GroupNorm-backward reductions (sum dXn, sum dXn xhat) from the weight-gradient pass instead of a pass over (dXn, x): semabs_wgrad_conv3_gn.
         self.wgrad_gn = os.environ.get("SEMABS_WGRAD_GN", "1") == "1"      # A/B: 0 = semabs_wgrad_conv3 + semabs_chan_reduce
-        self._wg_gn_ok = {}
         # ... and, the sums being known before the data gradient, the GroupNorm-backward apply as that convolution's epilogue: semabs_conv3d_gnbwd
         self.fuse_gn_apply = os.environ.get("SEMABS_FUSE_GN_APPLY", "1") == "1"      # A/B: 0 = semabs_conv3d + semabs_gn_bwd_apply
-        self._gnbwd_ok = {}
         self.mfma_wgrad = True          # tests / tuning: False = the fp32 VALU reduction kernel for every conv weight gradient
         self.debug = None               # tests: list collecting (tape kind, incoming gradient) during backward
         self.arena = _ZeroArena(self.dev)
@@ -168,124 +145,38 @@ class UNetTrainer:
         L = self.layouts
         L.invalidate()
         L.refresh_all()
+        p, c = self.p, self.convs
         for pre, kind, cin, cout in self.plan:
             key = self.prefix + pre
-            if kind in ("gcr", "gc"):
-                w = self.p[key + "conv.weight"]
-                k = w.shape[2]
-                fwd = L.get(key + "fwd", w, lambda t, cout=cout: _flat_packed(_pad32(t.permute(0, 2, 3, 4, 1).reshape(cout, -1))))
-                bwd = L.get(key + "bwd", w, lambda t, cin=cin: _flat_packed(_pad32(t.flip(2, 3, 4).permute(1, 2, 3, 4, 0).reshape(cin, -1))))
-                self.mats[pre] = dict(kind="conv", cin=cin, cout=cout, k=k, groups=self.G if cin >= self.G else 1, fwd=fwd, bwd=bwd)
-            elif kind == "convT":
-                w = self.p[key + "weight"]                                             # [cin, cout, 3, 3, 3]
+            if kind == "convT":
+                w = p[key + "weight"]                                                  # [cin, cout, 3, 3, 3]
+                c[pre] = _ConvT.of(pre, L.get(key + "fwd", w, convT_class_layout), L.get(key + "bwd", w, conv_fwd_layout), w.shape, p[key + "bias"])
+                continue
+            gn = kind in ("gcr", "gc")                                                 # else: the final 1x1x1 conv with bias
+            w = p[key + ("conv.weight" if gn else "weight")]
+            c[pre] = _Conv.of(pre, L.get(key + "fwd", w, conv_fwd_layout), L.get(key + "bwd", w, conv_bwd_layout), w.shape,
+                              p[key + "groupnorm.weight"] if gn else None, p[key + "groupnorm.bias"] if gn else None, None if gn else p[key + "bias"], self.G)
+        block = lambda pre: [c[pre + f"conv{j}."] for j in (1, 2, 3)]
+        n = len(self.f_maps)
+        self.enc = [block(f"encoders.{i}.basic_module.") for i in range(n)]
+        self.dec = [(c[f"decoders.{i}.upsampling.upsample."], block(f"decoders.{i}.basic_module.")) for i in range(n - 1)]
 
-                def classes(t):
-                    from .unet3d import _pack_fragments
-                    mats, packs, offs, off = [], [], [], 0
-                    for cls in range(8):
-                        pp = (cls >> 2, (cls >> 1) & 1, cls & 1)
-                        cols = []
-                        for t0 in range(pp[0] + 1):
-                            for t1 in range(pp[1] + 1):
-                                for t2 in range(pp[2] + 1):
-                                    kk = [1 if q == 0 else (0 if tt == 0 else 2) for q, tt in zip(pp, (t0, t1, t2))]
-                                    cols.append(t[:, :, kk[0], kk[1], kk[2]].t())
-                        m = torch.cat(cols, dim=1).contiguous()
-                        mats.append(m.reshape(-1)); packs.append(_pack_fragments(m)); offs.append(off); off += m.numel()
-                    return torch.cat(mats + packs), offs
-
-                hi, lo, offs = L.get(key + "fwd", w, classes)
-                bwd = L.get(key + "bwd", w, lambda t, cin=cin: _flat_packed(_pad32(t.permute(0, 2, 3, 4, 1).reshape(cin, -1))))   # [cin, (k, cout)]
-                self.mats[pre] = dict(kind="convT", cin=cin, cout=cout, fwd=(hi, lo, 512), class_off=(C.c_long * 8)(*offs), bwd=bwd)
-            else:                                                                      # final 1x1x1 conv with bias
-                w = self.p[key + "weight"]
-                fwd = L.get(key + "fwd", w, lambda t, cin=cin, cout=cout: _flat_packed(_pad32(t.reshape(cout, cin))))
-                bwd = L.get(key + "bwd", w, lambda t, cin=cin, cout=cout: _flat_packed(_pad32(t.reshape(cout, cin).t().contiguous())))
-                self.mats[pre] = dict(kind="final", cin=cin, cout=cout, k=1, fwd=fwd, bwd=bwd)
-
-    # ---- forward -----------------------------------------------------------------------------------------------------------------
+    # ---- forward: unet3d's launch sequence in exact mode, with a tape ------------------------------------------------------------
     def _conv_fwd(self, x, pre, relu, resid=None, in_sums=None, out_groups=0):
-        """-> (tape record, GroupNorm statistics of the output or None).  in_sums: statistics of x when its producer already has them
-        (scatter / the previous convolution / the transposed convolution: fused into their epilogues, no pass over x);
-        out_groups > 0: have this convolution produce the statistics of ITS output for the layer that follows."""
-        m = self.mats[pre]
-        key = self.prefix + pre
-        B, D0, D1, D2, Cc = x.shape
-        nvox, G, st = D0 * D1 * D2, m["groups"], _lib.stream()
+        """-> (tape record, GroupNorm statistics of the output or None); see unet3d.gn_conv."""
         r = _Rec()
-        r.name, r.x = pre, x
-        sums = in_sums
-        if sums is None:
-            sums = self.arena.zeros((B, G, 2), torch.float64)
-            _lib.call("semabs_gn_stats", _lib.ptr(x), _lib.ptr(sums), B, nvox, Cc, G, 1, st)
-        r.scale = torch.empty(B, Cc, dtype=torch.float32, device=self.dev)
-        r.shift = torch.empty_like(r.scale)
-        r.mean = torch.empty(B, G, dtype=torch.float32, device=self.dev)
-        r.rstd = torch.empty_like(r.mean)
-        _lib.call("semabs_gn_finalize", _lib.ptr(sums), _lib.ptr(self.p[key + "groupnorm.weight"]), _lib.ptr(self.p[key + "groupnorm.bias"]),
-                  _lib.ptr(r.scale), _lib.ptr(r.shift), B, Cc, G, nvox, 1e-5, st)
-        _lib.call("semabs_gn_meanrstd", _lib.ptr(sums), _lib.ptr(r.mean), _lib.ptr(r.rstd), B, G, nvox * (Cc // G), 1e-5, st)
-        r.y = torch.empty(B, D0, D1, D2, m["cout"], dtype=torch.float32, device=self.dev)
-        args = (_lib.ptr(x), _lib.ptr(m["fwd"][0]), _lib.ptr(m["fwd"][1]), _lib.ptr(r.y), _lib.ptr(r.scale), _lib.ptr(r.shift),
-                None, _lib.ptr(resid), B, D0, D1, D2, m["cin"], m["cout"], 3, int(relu), 1 | m["fwd"][2])
-        out_sums = None
-        if out_groups:
-            out_sums = self.arena.zeros((B, out_groups, 2), torch.float64)
-            _lib.call("semabs_conv3d_stats", *args, _lib.ptr(out_sums), out_groups, st)
-        else:
-            _lib.call("semabs_conv3d", *args, st)
-        return r, out_sums
-
-    def _block_fwd(self, x, pre, tape, in_sums=None):
-        # conv1 / conv2 hand the statistics of their outputs to the GroupNorm of conv2 / conv3 (like unet3d.ResidualUNet3D._block)
-        r1, s1 = self._conv_fwd(x, pre + "conv1.", True, in_sums=in_sums, out_groups=self.mats[pre + "conv2."]["groups"])
-        r2, s2 = self._conv_fwd(r1.y, pre + "conv2.", True, in_sums=s1, out_groups=self.mats[pre + "conv3."]["groups"])
-        r3, _ = self._conv_fwd(r2.y, pre + "conv3.", True, resid=r1.y, in_sums=s2)
-        tape.append(("block", r1, r2, r3))
-        return r3.y
+        _, sums = gn_conv(x, self.convs[pre], relu, self.arena.zeros, 1, resid=resid, in_sums=in_sums, out_groups=out_groups, rec=r)
+        return r, sums
 
     def forward(self, x: torch.Tensor, in_sums=None):
         """x fp32 [B, S, S, S, Cin] -> (y [B, S, S, S, Cout], tape).  in_sums: GroupNorm statistics of x (fp64 [B, groups, 2]) when the
         producer of x already has them (semabs_scatter_mean_stats)."""
         assert x.dtype == torch.float32 and x.is_contiguous()
-        st = _lib.stream()
         tape: List = []
-        L = len(self.f_maps)
-        feats = []
-        for i in range(L):
-            if i > 0:
-                B, D0, D1, D2, Cc = x.shape
-                y = torch.empty(B, D0 // 2, D1 // 2, D2 // 2, Cc, dtype=torch.float32, device=self.dev)
-                _lib.call("semabs_maxpool3d", _lib.ptr(x), _lib.ptr(y), B, D0, D1, D2, Cc, 1, st)
-                tape.append(("pool", x, i - 1))
-                x = y
-            x = self._block_fwd(x, f"encoders.{i}.basic_module.", tape, in_sums=in_sums if i == 0 else None)
-            feats.insert(0, x)
-        for i, skip in enumerate(feats[1:]):
-            pre = f"decoders.{i}.upsampling.upsample."
-            m = self.mats[pre]
-            B, D0, D1, D2, _ = x.shape
-            y = torch.empty_like(skip)
-            blk = f"decoders.{i}.basic_module."
-            og = self.mats[blk + "conv1."]["groups"]
-            sums = self.arena.zeros((B, og, 2), torch.float64)
-            _lib.call("semabs_convtranspose3d_stats", _lib.ptr(x), _lib.ptr(m["fwd"][0]), _lib.ptr(m["fwd"][1]), m["class_off"], _lib.ptr(y),
-                      _lib.ptr(self.p[self.prefix + pre + "bias"]), _lib.ptr(skip), B, D0, D1, D2, m["cin"], m["cout"], 1 | m["fwd"][2],
-                      _lib.ptr(sums), og, st)
-            tape.append(("up", pre, x, L - 2 - i))
-            x = self._block_fwd(y, blk, tape, in_sums=sums)
-        m = self.mats["final_conv."]
-        B, D0, D1, D2, _ = x.shape
-        y = torch.empty(B, D0, D1, D2, m["cout"], dtype=torch.float32, device=self.dev)
+        fin = self.convs["final_conv."]
         wf = self.p[self.prefix + "final_conv.weight"].detach()
-        if self.rows_linear and m["cin"] % 4 == 0 and m["cout"] <= 128 and wf.is_contiguous():
-            # the 1 x 1 x 1 convolution IS a row-linear layer over the voxels: semabs_linear_rows streams it at HBM speed (the gather kernel: 1.28 ms at 8 x 128^3)
-            _lib.call("semabs_linear_rows", _lib.ptr(x), m["cin"], _lib.ptr(wf), m["cin"], 1, _lib.ptr(self.p[self.prefix + "final_conv.bias"]), _lib.ptr(y),
-                      B * D0 * D1 * D2, m["cin"], m["cout"], 0, 0.0, None, None, None, None, None, None, st)
-        else:
-            _lib.call("semabs_conv3d", _lib.ptr(x), _lib.ptr(m["fwd"][0]), _lib.ptr(m["fwd"][1]), _lib.ptr(y), None, None,
-                      _lib.ptr(self.p[self.prefix + "final_conv.bias"]), None, B, D0, D1, D2, m["cin"], m["cout"], 1, 0, 1 | m["fwd"][2], st)
-        tape.append(("final", x))
+        rows = self.rows_linear and fin.cin % 4 == 0 and fin.cout <= 128 and wf.is_contiguous()
+        y = unet_forward(x, self.enc, self.dec, fin, self.arena.zeros, 1, in_sums=in_sums, tape=tape, rows_w=wf if rows else None)
         return y, tape
 
     # ---- backward ----------------------------------------------------------------------------------------------------------------
@@ -295,34 +186,13 @@ class UNetTrainer:
         _lib.call("semabs_chan_reduce", _lib.ptr(a2d), None, None, None, _lib.ptr(red), 1, R, Cc, 1, _lib.stream())
         grad.add_(red[0, :, 0].float())
 
-    def _wgrad_conv3_route(self, D0, D1, D2, ca, cx, scratch_floats) -> int:
-        key = (D0, D1, D2, ca, cx, scratch_floats)
-        r = self._wg_routes.get(key)
+    def _supported(self, entry: str, *args) -> int:
+        """Memoised answer of the library's own routing predicate `entry` (semabs_*_supported: the arguments, then an int out)."""
+        r = self._routes.get((entry,) + args)
         if r is None:
-            import ctypes as C
             k = C.c_int(0)
-            _lib.call("semabs_wgrad_conv3_supported", D0, D1, D2, ca, cx, int(scratch_floats), C.byref(k))
-            r = self._wg_routes[key] = int(k.value)
-        return r
-
-    def _wgrad_conv3_gn_ok(self, B, D0, D1, D2, ca, cx, scratch_floats) -> bool:
-        key = (B, D0, D1, D2, ca, cx, scratch_floats)
-        r = self._wg_gn_ok.get(key)
-        if r is None:
-            import ctypes as C
-            k = C.c_int(0)
-            _lib.call("semabs_wgrad_conv3_gn_supported", B, D0, D1, D2, ca, cx, int(scratch_floats), C.byref(k))
-            r = self._wg_gn_ok[key] = bool(k.value)
-        return r
-
-    def _conv3d_gnbwd_ok(self, B, D0, D1, D2, cin_conv, cout_conv, G, have_add) -> bool:
-        key = (B, D0, D1, D2, cin_conv, cout_conv, G, have_add)
-        r = self._gnbwd_ok.get(key)
-        if r is None:
-            import ctypes as C
-            k = C.c_int(0)
-            _lib.call("semabs_conv3d_gnbwd_supported", B, D0, D1, D2, cin_conv, cout_conv, G, 1 if have_add else 0, C.byref(k))
-            r = self._gnbwd_ok[key] = bool(k.value)
+            _lib.call(entry, *args, C.byref(k))
+            r = self._routes[(entry,) + args] = int(k.value)
         return r
 
     def _wg_scratch(self):
@@ -351,12 +221,6 @@ class UNetTrainer:
         _lib.call("semabs_ew", _lib.ptr(a), _lib.ptr(inv), _lib.ptr(out), a.numel(), 3, 0.0, None, _lib.stream())
         return out
 
-    def _unscale(self, a, s2):
-        out = torch.empty_like(a)
-        inv = s2[1:]
-        _lib.call("semabs_ew", _lib.ptr(a), _lib.ptr(inv), _lib.ptr(out), a.numel(), 3, 0.0, None, _lib.stream())
-        return out
-
     def _ew(self, a, b, mode, want_max=False, in_scale=None):
         """in_scale (device scalar): a still carries a producer's dynamic gradient scale; multiply by in_scale[0] on the way in (saves the
         separate un-scaling pass over a)."""
@@ -375,10 +239,10 @@ class UNetTrainer:
         (+ add1).  relu_in: the layer's input r.x is a post-ReLU activation and the caller wants the gradient in front of that
         ReLU (masked by r.x > 0, with its max |.| recorded for the next dynamic scale).  Accumulates the conv weight and GroupNorm
         affine gradients."""
-        m = self.mats[r.name]
+        m = self.convs[r.name]
         key = self.prefix + r.name
         B, D0, D1, D2, cin = r.x.shape
-        cout, nvox, G, st = m["cout"], D0 * D1 * D2, m["groups"], _lib.stream()
+        cout, nvox, G, st = m.cout, D0 * D1 * D2, m.groups, _lib.stream()
         sc, sh, s2 = self._scale(dZ, B, cout)                # dynamic power-of-two scale of dZ, shared by the weight and data gradients
         inv = s2[1:]
         dW = self.g[key + "conv.weight"]                     # [cout, cin, 3, 3, 3]: the kernels accumulate in this layout directly
@@ -387,13 +251,13 @@ class UNetTrainer:
         scr = self._wg_scratch() if self.wgrad_tr else (None, 0)
         red = self.arena.zeros((B, cin, 2), torch.float64)
         have_red = False
-        if self.mfma_wgrad and self.wgrad_tr and self.wgrad_gn and self._wgrad_conv3_gn_ok(B, D0, D1, D2, cout, cin, scr[1]):
+        if self.mfma_wgrad and self.wgrad_tr and self.wgrad_gn and self._supported("semabs_wgrad_conv3_gn_supported", B, D0, D1, D2, cout, cin, int(scr[1])):
             # one pass over (dZ, x): the weight gradient AND the (sum dXn, sum dXn xhat) the GroupNorm backward needs (csrc/train.hip has the algebra)
             _lib.call("semabs_wgrad_conv3_gn", _lib.ptr(dZ), _lib.ptr(r.x), _lib.ptr(r.mean), _lib.ptr(r.rstd), G, _lib.ptr(self.p[key + "groupnorm.weight"]),
                       _lib.ptr(self.p[key + "groupnorm.bias"]), _lib.ptr(self.p[key + "conv.weight"]), _lib.ptr(s2), _lib.ptr(dW), _lib.ptr(red),
                       B, D0, D1, D2, cout, cin, *scr, st)
             have_red = True
-        elif self.mfma_wgrad and self._wgrad_conv3_route(D0, D1, D2, cout, cin, scr[1]):
+        elif self.mfma_wgrad and self._supported("semabs_wgrad_conv3_supported", D0, D1, D2, cout, cin, int(scr[1])):
             _lib.call("semabs_wgrad_conv3", _lib.ptr(dZ), _lib.ptr(r.x), _lib.ptr(r.scale), _lib.ptr(r.shift), _lib.ptr(s2), _lib.ptr(dW),
                       B, D0, D1, D2, cout, cin, 1, *scr, st)
         elif cin % 16 == 0 and self.mfma_wgrad:                  # 8^3 / 4^3 levels: rows through LDS, transposing reads (k_wgrad_mfma)
@@ -402,7 +266,7 @@ class UNetTrainer:
         else:
             _lib.call("semabs_wgrad", _lib.ptr(dZ), _lib.ptr(r.x), _lib.ptr(r.scale), _lib.ptr(r.shift), _lib.ptr(dW), B, D0, D1, D2, D0, D1, D2, 1,
                       cout, cin, 27, TAPS_CONV3, 1, st)
-        if have_red and self.fuse_gn_apply and self._conv3d_gnbwd_ok(B, D0, D1, D2, cout, cin, G, add1 is not None):
+        if have_red and self.fuse_gn_apply and self._supported("semabs_conv3d_gnbwd_supported", B, D0, D1, D2, cout, cin, G, int(add1 is not None)):
             # the sums are known BEFORE the data gradient (they came out of the weight-gradient pass), so the GroupNorm backward can be the data-gradient
             # convolution's epilogue: no dXn tensor, no apply pass (read dXn, read x, write dX)
             coef = torch.empty(B, cin, 3, dtype=torch.float32, device=self.dev)
@@ -410,14 +274,14 @@ class UNetTrainer:
                       _lib.ptr(self.g[key + "groupnorm.weight"]), _lib.ptr(self.g[key + "groupnorm.bias"]), B, cin, G, nvox, st)
             dX = torch.empty(B, D0, D1, D2, cin, dtype=torch.float32, device=self.dev)
             bits = self.arena.zeros((1,), torch.int32)
-            _lib.call("semabs_conv3d_gnbwd", _lib.ptr(dZ), _lib.ptr(m["bwd"][0]), _lib.ptr(m["bwd"][1]), _lib.ptr(dX), _lib.ptr(sc), _lib.ptr(sh), _lib.ptr(r.x),
+            _lib.call("semabs_conv3d_gnbwd", _lib.ptr(dZ), _lib.ptr(m.bwd[0]), _lib.ptr(m.bwd[1]), _lib.ptr(dX), _lib.ptr(sc), _lib.ptr(sh), _lib.ptr(r.x),
                       _lib.ptr(r.mean), _lib.ptr(r.rstd), _lib.ptr(coef), G, _lib.ptr(add1), 1 if relu_in else 0, _lib.ptr(bits), B, D0, D1, D2, cout, cin,
-                      1 | m["bwd"][2], st)
+                      1 | m.bwd[2], st)
             dX._semabs_absmax = bits
             return dX
         dXn = torch.empty(B, D0, D1, D2, cin, dtype=torch.float32, device=self.dev)      # = s * (d loss / d GN output)
-        _lib.call("semabs_conv3d", _lib.ptr(dZ), _lib.ptr(m["bwd"][0]), _lib.ptr(m["bwd"][1]), _lib.ptr(dXn), _lib.ptr(sc), _lib.ptr(sh), None, None,
-                  B, D0, D1, D2, cout, cin, 3, 0, 1 | m["bwd"][2], st)
+        _lib.call("semabs_conv3d", _lib.ptr(dZ), _lib.ptr(m.bwd[0]), _lib.ptr(m.bwd[1]), _lib.ptr(dXn), _lib.ptr(sc), _lib.ptr(sh), None, None,
+                  B, D0, D1, D2, cout, cin, 3, 0, 1 | m.bwd[2], st)
         if not have_red:
             _lib.call("semabs_chan_reduce", _lib.ptr(dXn), _lib.ptr(r.x), _lib.ptr(r.mean), _lib.ptr(r.rstd), _lib.ptr(red), B, nvox, cin, G, st)
         coef = torch.empty(B, cin, 3, dtype=torch.float32, device=self.dev)
@@ -444,11 +308,11 @@ class UNetTrainer:
 
     def _up_bwd(self, pre: str, xin: torch.Tensor, g: torch.Tensor):
         """ConvTranspose3d k3 s2 p1 op1 backward: g = gradient w.r.t. its output [B, 2D, 2D, 2D, cout] -> gradient w.r.t. xin."""
-        m = self.mats[pre]
+        m = self.convs[pre]
         key = self.prefix + pre
         st = _lib.stream()
         B, D0, D1, D2, cin = xin.shape
-        cout = m["cout"]
+        cout = m.cout
         self._colsum(g.view(-1, cout), self.g[key + "bias"])
         sc, sh, s2 = self._scale(g, B, cout)
         if cout % 16 == 0 and self.mfma_wgrad:
@@ -458,8 +322,8 @@ class UNetTrainer:
             _lib.call("semabs_wgrad", _lib.ptr(xin), _lib.ptr(g), None, None, _lib.ptr(self.g[key + "weight"]), B, D0, D1, D2, 2 * D0, 2 * D1, 2 * D2, 2,
                       cin, cout, 27, TAPS_CONV3, 1, st)
         dx = torch.empty(B, D0, D1, D2, cin, dtype=torch.float32, device=self.dev)
-        _lib.call("semabs_conv3d_gather", _lib.ptr(g), _lib.ptr(m["bwd"][0]), _lib.ptr(m["bwd"][1]), _lib.ptr(dx), _lib.ptr(sc), _lib.ptr(sh),
-                  B, 2 * D0, 2 * D1, 2 * D2, D0, D1, D2, 2, cout, cin, 27, TAPS_CONV3, 1 | m["bwd"][2], st)
+        _lib.call("semabs_conv3d_gather", _lib.ptr(g), _lib.ptr(m.bwd[0]), _lib.ptr(m.bwd[1]), _lib.ptr(dx), _lib.ptr(sc), _lib.ptr(sh),
+                  B, 2 * D0, 2 * D1, 2 * D2, D0, D1, D2, 2, cout, cin, 27, TAPS_CONV3, 1 | m.bwd[2], st)
         return dx, s2[1:]                                    # still scaled: the block that consumes it multiplies by 1 / s in its first pass
 
     def backward(self, tape, dy: torch.Tensor, on_done=None) -> torch.Tensor:
@@ -477,9 +341,9 @@ class UNetTrainer:
                 self.debug.append((kind, g))
             if kind == "final":
                 x = item[1]
-                m = self.mats["final_conv."]
+                m = self.convs["final_conv."]
                 B, D0, D1, D2, cin = x.shape
-                cout = m["cout"]
+                cout = m.cout
                 R = B * D0 * D1 * D2
                 _lib.call("semabs_wgrad", _lib.ptr(g), _lib.ptr(x), None, None, _lib.ptr(self.g[self.prefix + "final_conv.weight"]), 1, 1, 1, R, 1, 1, R, 1,
                           cout, cin, 1, TAPS_ONE, 1, st)
@@ -500,8 +364,8 @@ class UNetTrainer:
                     g, g_scale = dx, None
                     continue
                 else:
-                    _lib.call("semabs_conv3d", _lib.ptr(g), _lib.ptr(m["bwd"][0]), _lib.ptr(m["bwd"][1]), _lib.ptr(dx), _lib.ptr(sc), _lib.ptr(sh), None, None,
-                              B, D0, D1, D2, cout, cin, 1, 0, 1 | m["bwd"][2], st)
+                    _lib.call("semabs_conv3d", _lib.ptr(g), _lib.ptr(m.bwd[0]), _lib.ptr(m.bwd[1]), _lib.ptr(dx), _lib.ptr(sc), _lib.ptr(sh), None, None,
+                              B, D0, D1, D2, cout, cin, 1, 0, 1 | m.bwd[2], st)
                 g, g_scale = dx, s2[1:]
             elif kind == "block":
                 g = self._block_bwd(item[1:], g, in_scale=g_scale)
@@ -670,8 +534,7 @@ class VOOLTrainer:
             _lib.call("semabs_linear_rows", _lib.ptr(x), Ci, _lib.ptr(wd), 1 if transposed else wd.shape[1], wd.shape[1] if transposed else 1,
                       _lib.ptr(b), _lib.ptr(y), R, Ci, Co, 1 if act else 0, SLOPE, _lib.ptr(s2), None, None, None, None, None, _lib.stream())
             return (y, s2[1:]) if grad_in else y
-        hi, lo, pk = self.unet.layouts.get(f"lin:{wkey}:{int(transposed)}", w, (lambda t: _flat_packed(_pad32(t.t().contiguous()))) if transposed else
-                                           (lambda t: _flat_packed(_pad32(t.contiguous()))))
+        hi, lo, pk = self.unet.layouts.get(f"lin:{wkey}:{int(transposed)}", w, lambda t: linear_layout(t, transposed))
         y = torch.empty(R, Co, dtype=torch.float32, device=self.dev)
         u = self.unet
         sc = sh = s2 = None
@@ -729,7 +592,7 @@ class VOOLTrainer:
         head = torch.full((nvox,), -1, dtype=torch.int32, device=dev)
         nxt = torch.empty(N, dtype=torch.int32, device=dev)
         sums = None
-        if self.C == 16 and u.mats["encoders.0.basic_module.conv1."]["groups"] == 8:      # first GroupNorm's statistics come out of the scatter
+        if self.C == 16 and u.convs["encoders.0.basic_module.conv1."].groups == 8:      # first GroupNorm's statistics come out of the scatter
             sums = u.arena.zeros((P, 8, 2), torch.float64)
             _lib.call("semabs_scatter_mean_stats", _lib.ptr(flat), _lib.ptr(pf), _lib.ptr(head), _lib.ptr(nxt), _lib.ptr(vol), P, N, self.C, nvox, 1,
                       _lib.ptr(sums), st)

@@ -176,3 +176,30 @@ def test_pack_fragments_layout():
                 for e in (0, 3, 7):
                     assert p[ks, cb, lane, e] == w[cb * 16 + row, ks * 32 + kg * 8 + e]
     assert p.numel() == w.numel()
+
+
+def test_weight_layouts_commute_with_gather():
+    """The property train._WeightLayouts relies on: every layout function of unet3d is pure data movement, so running it on an index tensor
+    (1 .. numel, 0 = padding) and gathering the weights through the result equals running it on the weights - same flag word, same class offsets.
+    Also pins the packing conditions: a convolution packs when Cout % 16 == 0, a transposed convolution only when every class matrix can be
+    (Cout % 16 == 0 and Cin % 32 == 0: the Cin = 16 one comes out unpacked, flag 0, on the inference side too)."""
+    import torch
+    from semabs_amd.unet3d import _ConvT, conv_bwd_layout, conv_fwd_layout, convT_class_layout, linear_layout
+    g = torch.Generator().manual_seed(0)
+    cases = [(conv_fwd_layout, (16, 16, 3, 3, 3), 512), (conv_fwd_layout, (32, 16, 3, 3, 3), 512), (conv_fwd_layout, (16, 1, 3, 3, 3), 512),
+             (conv_fwd_layout, (8, 16, 1, 1, 1), 0), (conv_fwd_layout, (16, 16, 1, 1, 1), 512),
+             (conv_bwd_layout, (32, 16, 3, 3, 3), 512), (conv_bwd_layout, (16, 1, 3, 3, 3), 0), (conv_bwd_layout, (8, 16, 1, 1, 1), 512),
+             (convT_class_layout, (32, 16, 3, 3, 3), 512), (convT_class_layout, (16, 16, 3, 3, 3), 0), (convT_class_layout, (64, 24, 3, 3, 3), 0),
+             (linear_layout, (128, 128), 512), (linear_layout, (16, 128), 512), (linear_layout, (35, 32), 0),
+             (lambda t: linear_layout(t, True), (16, 128), 512), (lambda t: linear_layout(t, True), (64, 36), 0)]
+    for layout, shape, flag in cases:
+        w = torch.randn(*shape, generator=g)
+        idx = torch.arange(1, w.numel() + 1, dtype=torch.int32).view(shape)
+        flat_w, *extra_w = layout(w)
+        flat_i, *extra_i = layout(idx)
+        assert flat_i.dtype == torch.int32 and extra_w == extra_i and extra_w[0] == flag, (shape, extra_w)
+        gathered = torch.cat([torch.zeros(1), w.reshape(-1)])[flat_i.long()]
+        assert torch.equal(gathered, flat_w), shape
+        assert flat_w.numel() % 32 == 0
+    ct = _ConvT(torch.randn(16, 16, 3, 3, 3, generator=g), torch.zeros(16), "cpu")
+    assert ct.packed == 0 and ct.w_hi.numel() == 27 * 16 * 16 and list(ct.class_off) == [0, 256, 768, 1280, 2304, 2816, 3840, 4864]
